@@ -133,7 +133,17 @@ def parse_args():
     ap.add_argument("--no-end-to-end", action="store_true",
                     help="N = 1 only: skip the PCIe-inclusive timing of the "
                          "host-pointer family (HBVEdu.simulate, 100k sets)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one "
+                         "computed as DIR/<name>.npy (float64): the "
+                         "all-gathered scores and rank 0's qsim / state "
+                         "series, a fixed seeded sample of sets (and rows) "
+                         "where the whole would exceed 64 MB in all; "
+                         "DIR/manifest.json says what was kept")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -1015,7 +1025,8 @@ def run_workload(args, device, rank, world, on_host, steps, warmup,
     digest = hashlib.sha1(scores.detach().cpu().numpy().tobytes()).hexdigest()
     bytes_per_step = {"qsim": 8, "metric": 0,
                       "storages": ALL_OUT_BYTES[args.model]}[args.mode]
-    return dict(steps=steps, digest=digest, first=first, ens=ens, sweep=sweep,
+    return dict(steps=steps, digest=digest, scores=scores, first=first,
+                ens=ens, sweep=sweep,
                 params_host=params_host, qsim=qsim,
                 qobs=qobs, f=f, name=name, scaling=scaling, n=n, t=t,
                 total_units=total_units, elapsed=elapsed, kernel_ms=kernel_ms,
@@ -1276,6 +1287,71 @@ def write_detail(full):
     return None
 
 
+DUMP_LIMIT = 64 << 20          # bytes of all arrays --dump-outputs writes
+DUMP_SEED = 20240607           # the sample of sets / rows where one is taken
+
+
+def _listed(idx, of):
+    """Sampled indices for the manifest: the list itself while it is short."""
+    if idx.size <= 65536:
+        return idx.tolist()
+    return "%d of %d, sorted (numpy default_rng(seed), arrays in manifest " \
+           "order)" % (idx.size, of)
+
+
+def _sample(a, limit, rng):
+    """Host float64 copy of device tensor `a` (parameter sets on its last
+    axis) within `limit` bytes: every set if they fit, else a sorted seeded
+    sample of them; if even one set's series is too large, flattened to
+    [rows, sets] with a sorted seeded sample of the rows as well."""
+    import torch
+    a = a.detach()
+    n = a.shape[-1]
+    rows = a.numel() // max(n, 1)
+    rec = {"shape": list(a.shape)}
+    k = max(1, min(n, limit // (8 * max(rows, 1))))
+    if k < n:
+        cols = np.sort(rng.choice(n, k, replace=False))
+        a = a.index_select(-1, torch.from_numpy(cols).to(a.device))
+        rec["sets"] = _listed(cols, n)
+    if rows * k * 8 > limit:
+        keep = np.sort(rng.choice(rows, max(1, limit // (8 * k)),
+                                  replace=False))
+        a = a.reshape(rows, k).index_select(
+            0, torch.from_numpy(keep).to(a.device))
+        rec["rows_of_flattened"] = _listed(keep, rows)
+    out = a.cpu().numpy().astype(np.float64, copy=False)
+    rec["written_shape"] = list(out.shape)
+    return out, rec
+
+
+def dump_outputs(folder, r):
+    """What the last timed step handed its caller, as DIR/<name>.npy: the
+    all-gathered per-set scores, and rank 0's qsim and state series where
+    the mode writes them -- at most DUMP_LIMIT bytes in all, the same sample
+    for the same arguments on every run."""
+    os.makedirs(folder, exist_ok=True)
+    series = []
+    if r["sweep"].qsim is not None:
+        series.append(("qsim", r["sweep"].qsim))
+    st = r["sweep"].storages
+    if st is not None:
+        st = st if isinstance(st, (tuple, list)) else (st,)
+        series += [("storage%d" % k, s) for k, s in enumerate(st)]
+    rng = np.random.default_rng(DUMP_SEED)
+    scores_limit = DUMP_LIMIT // 4 if series else DUMP_LIMIT
+    arrays = [("scores", r["scores"], scores_limit)]
+    each = (DUMP_LIMIT - scores_limit) // max(len(series), 1)
+    arrays += [(name, s, each) for name, s in series]
+    manifest = {}
+    for name, a, limit in arrays:
+        host, manifest[name] = _sample(a, limit, rng)
+        np.save(os.path.join(folder, name + ".npy"), host)
+    with open(os.path.join(folder, "manifest.json"), "w") as fh:
+        json.dump({"steps": r["steps"], "seed": DUMP_SEED,
+                   "arrays": manifest}, fh, indent=1)
+
+
 def main():
     args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1296,6 +1372,10 @@ def main():
               % (args.gpus, world), file=sys.stderr)
     if args.share_gpu:
         local_rank = 0
+    if local_rank >= torch.cuda.device_count():
+        sys.exit("bench.py: rank %d has no GPU of its own (%d visible): "
+                 "one rank per GPU; --backend gloo --share-gpu puts several "
+                 "ranks on one" % (rank, torch.cuda.device_count()))
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
     if world > 1:
@@ -1316,6 +1396,10 @@ def main():
 
     r = run_workload(args, device, rank, world, on_host, args.steps,
                      args.warmup, score=args.score)
+    assert r["steps"] == args.steps
+    if args.dump_outputs and rank == 0:
+        # before the power soak sweeps the same buffers again
+        dump_outputs(args.dump_outputs, r)
     n, t, kernel_ms = r["n"], r["t"], r["kernel_ms"]
     r["power"] = (None if args.no_power_soak else
                   power_soak(r["sweep"], r["elapsed"] / args.steps, device,

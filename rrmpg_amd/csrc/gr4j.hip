@@ -475,6 +475,17 @@ thread_local TierStreams *tl_tier_now = nullptr;
 }  // namespace
 int rr_tier_fork(hipStream_t st)
 {
+    // A launch into a stream capture keeps its tier kernels on `st`: the
+    // graph is then one chain like every other *_simulate_dev capture.  The
+    // branches the fork makes segfaulted hipGraphLaunch on the host
+    // (test_dev_sweeps_capture_into_a_hip_graph[hystgr4j]).
+    hipStreamCaptureStatus capture = hipStreamCaptureStatusNone;
+    tl_tier_now = nullptr;
+    if (hipStreamIsCapturing(st, &capture) != hipSuccess) {
+        (void)hipGetLastError();
+        return RR_OK;
+    }
+    if (capture != hipStreamCaptureStatusNone) return RR_OK;
     tl_tier_now = tier_streams();
     if (!tl_tier_now) {
         (void)hipGetLastError();

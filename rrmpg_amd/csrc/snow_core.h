@@ -18,8 +18,8 @@ size_t rr_gr4j_uh_scratch_bytes(int64_t N, double max_x4);
 // each with a fraction of the GPU.  rr_tier_fork makes the calling thread's
 // side streams of the current device wait for what `st` holds so far,
 // rr_tier_stream(k) hands out side stream k (0..2), rr_tier_join makes `st`
-// wait for all of them.  Events only: nothing blocks the host, and a stream
-// capture of `st` follows the fork into the side streams.
+// wait for all of them.  Events only: nothing blocks the host.  A launch into
+// a stream capture of `st` does not fork: its tier kernels stay on `st`.
 int rr_tier_fork(hipStream_t st);
 hipStream_t rr_tier_stream(int k);
 int rr_tier_join(hipStream_t st);

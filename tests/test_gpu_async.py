@@ -351,9 +351,10 @@ def test_host_family_context_and_staged_gather(env, oracle):
 def test_dev_sweeps_capture_into_a_hip_graph(env, which):
     """Nothing in a *_simulate_dev call allocates, copies back or waits: a
     whole sweep -- pre-pass, plan, the tier kernels (for a sorted score-only
-    sweep of the hysteresis coupling: on side streams forked from and joined
-    to the caller's with events), the reference kernel -- captures into ONE
-    HIP graph, and its replays give the bits of the plain call."""
+    sweep of the hysteresis coupling: on side streams in the plain call, on
+    the caller's stream under capture, csrc/gr4j.hip rr_tier_fork), the
+    reference kernel -- captures into ONE HIP graph, and its replays give the
+    bits of the plain call."""
     torch, dev, models, syn, f = env
     t = 400
     if which == "hbvedu":

@@ -74,6 +74,41 @@ def test_single_gpu_line():
     assert c["unit"] == "model-timesteps/s" and "sets" in c["sample"]
 
 
+def test_dump_outputs_are_the_same_on_every_run(tmp_path):
+    """--dump-outputs DIR: the last timed step's scores and a fixed sample of
+    its qsim columns, float64, within 64 MB; two runs with the same arguments
+    write the same arrays, and the scores are those the line digests."""
+    import hashlib
+    import numpy as np
+    common = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2",
+              "--warmup", "1", "--sets", "20000", "--days", "800",
+              "--no-extra-configs", "--no-cpu-baseline", "--no-power-soak",
+              "--live-counters", "none"]
+    got = []
+    for k in range(2):
+        d = _run(common + ["--dump-outputs", str(tmp_path / str(k))])
+        assert d["steps"] == 2
+        with open(tmp_path / str(k) / "manifest.json") as fh:
+            man = json.load(fh)
+        assert man["steps"] == 2 and sorted(man["arrays"]) == ["qsim",
+                                                              "scores"]
+        arrays = {n: np.load(tmp_path / str(k) / (n + ".npy"))
+                  for n in man["arrays"]}
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert arrays["scores"].shape == (20000,)
+        assert hashlib.sha1(arrays["scores"].tobytes()).hexdigest() \
+            == d["scores_digest"]
+        # 128 MB of qsim: a sorted sample of its columns
+        sets = man["arrays"]["qsim"]["sets"]
+        assert sets == sorted(set(sets)) and len(sets) < 20000
+        assert arrays["qsim"].shape == (800, len(sets))
+        assert np.isfinite(arrays["qsim"]).all()
+        got.append(arrays)
+    for n in got[0]:
+        assert np.array_equal(got[0][n], got[1][n]), n
+
+
 def test_default_line_carries_every_config_and_the_valu_roof():
     """The driver's command (default workload = BASELINE.json's metric
     configuration): besides the headline fields the line holds the other
@@ -158,27 +193,29 @@ def test_default_line_carries_every_config_and_the_valu_roof():
     assert ee["cfg3_gpus8_over_8_shards"] < 1.6
 
 
-def test_eight_ranks_rehearsal_on_one_gpu():
-    """As far as one GPU allows towards the 8-GPU job: the driver's launch
-    line with eight ranks sharing the device over gloo, a ragged total of
-    1,000,003 sets, strong scaling.  The partition is shard_bounds', and the
-    all-gathered scores are those of the single-rank sweep, bit for bit (the
-    ranks draw their rows of ONE Philox population)."""
+def test_four_ranks_rehearsal_on_one_gpu():
+    """As far as one shared GPU allows towards the 8-GPU job: the driver's
+    launch line with four ranks sharing the device over gloo (with the
+    launcher and this process, six processes have the device open -- no more
+    may share one GPU), a ragged total of 1,000,003 sets, strong scaling.
+    The partition is shard_bounds', and the all-gathered scores are those of
+    the single-rank sweep, bit for bit (the ranks draw their rows of ONE
+    Philox population)."""
     from rrmpg_amd.sharding import shard_bounds
     common = ["--steps", "2", "--warmup", "1", "--sets", "1000003", "--mode",
               "metric", "--no-extra-configs", "--no-cpu-baseline",
               "--no-parity-spot", "--no-power-soak", "--live-counters", "none"]
     one = _run([sys.executable, "bench.py", "--gpus", "1"] + common)
     d = _run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
-              "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-              "--master-port", "29583", "bench.py", "--gpus", "8",
+              "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
+              "--master-port", "29583", "bench.py", "--gpus", "4",
               "--backend", "gloo", "--share-gpu"] + common,
              env={"HSA_ENABLE_IPC_MODE_LEGACY": "0"})
-    assert d["n_gpus"] == 8 and d["scaling"] == "strong"
+    assert d["n_gpus"] == 4 and d["scaling"] == "strong"
     assert d["config"]["sets_total"] == 1000003
-    assert d["config"]["shards"] == [list(shard_bounds(1000003, 8, r))
-                                     for r in range(8)]
-    assert d["config"]["sets_per_gpu"] == 125001       # rank 0: a longer block
+    assert d["config"]["shards"] == [list(shard_bounds(1000003, 4, r))
+                                     for r in range(4)]
+    assert d["config"]["sets_per_gpu"] == 250001       # rank 0: a longer block
     assert d["scores_finite"] is True
     assert d["scores_digest"] == one["scores_digest"]
     units = 1000003 * 10957 * 2
@@ -221,13 +258,23 @@ def test_self_launched_ranks_strong_scaling():
 
 
 def test_self_launched_ranks_over_rccl():
-    """The product path: one GPU per rank, backend nccl (= RCCL)."""
+    """The product path: one GPU per rank, backend nccl (= RCCL).  With one
+    GPU the second rank has none of its own: the job is refused at once,
+    naming the rehearsal that fits one GPU."""
     import torch
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "2",
+           "--warmup", "1", "--sets", "40000", "--days", "800"]
+    env = {"WORLD_SIZE": None, "RANK": None, "LOCAL_RANK": None}
     if torch.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs")
-    d = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "2",
-              "--warmup", "1", "--sets", "40000", "--days", "800"],
-             env={"WORLD_SIZE": None, "RANK": None, "LOCAL_RANK": None})
+        e = {k: v for k, v in os.environ.items() if k not in env}
+        out = subprocess.run(cmd, cwd=REPO, env=e, capture_output=True,
+                             text=True, timeout=300)
+        assert out.returncode != 0
+        assert "rank 1 has no GPU of its own (1 visible)" in out.stderr, \
+            out.stderr[-2000:]
+        assert "--share-gpu" in out.stderr
+        return
+    d = _run(cmd, env=env)
     assert d["n_gpus"] == 2 and d["scores_finite"] is True
     assert 0 <= d["parity_spot"] < 1e-10
 
@@ -462,18 +509,21 @@ def test_c_abi_allgather_over_rccl_on_one_rank(tmp_path):
 
 def test_c_abi_allgather_over_rccl_two_ranks(tmp_path):
     """Two processes, one GPU each, ragged blocks (1001 scores: 501 + 500):
-    the id travels through a file, every rank ends with the whole vector."""
+    the id travels through a file, every rank ends with the whole vector.
+    With one GPU both ranks sit on it: RCCL runs one rank per device, and
+    rr_comm_init refuses the communicator in both processes (RR_E_HIP, the
+    reason in rr_last_error) instead of hanging."""
     import torch
-    if torch.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs")
+    shared = torch.cuda.device_count() < 2
     script = tmp_path / "abi_two_ranks.py"
     script.write_text(
         "import ctypes, os, sys, time, torch\n"
         "sys.path.insert(0, %r)\n"
         "from rrmpg_amd import _lib\n"
-        "rank, idfile = int(sys.argv[1]), sys.argv[2]\n"
+        "rank, idfile, shared = int(sys.argv[1]), sys.argv[2], "
+        "sys.argv[3] == '1'\n"
         "lib = _lib.load()\n"
-        "torch.cuda.set_device(rank)\n"
+        "torch.cuda.set_device(0 if shared else rank)\n"
         "ident = (ctypes.c_char * 128)()\n"
         "if rank == 0:\n"
         "    assert lib.rr_comm_unique_id(ident) == 0, lib.rr_last_error()\n"
@@ -483,12 +533,19 @@ def test_c_abi_allgather_over_rccl_two_ranks(tmp_path):
         "    while not os.path.exists(idfile): time.sleep(0.05)\n"
         "    ident = (ctypes.c_char * 128).from_buffer_copy("
         "open(idfile, 'rb').read())\n"
-        "comm = ctypes.c_void_p()\n"
-        "assert lib.rr_comm_init(ctypes.byref(comm), 2, rank, ident) == 0, "
-        "lib.rr_last_error()\n"
         "n = 1001\n"
         "a, b = ctypes.c_int64(), ctypes.c_int64()\n"
         "lib.rr_shard_bounds(n, 2, rank, ctypes.byref(a), ctypes.byref(b))\n"
+        "assert (a.value, b.value) == ((0, 501), (501, 1001))[rank]\n"
+        "comm = ctypes.c_void_p()\n"
+        "rc = lib.rr_comm_init(ctypes.byref(comm), 2, rank, ident)\n"
+        "if shared:\n"
+        "    err = lib.rr_last_error()\n"
+        "    assert rc == -3 and comm.value is None, (rc, err)\n"
+        "    assert err.startswith(b'ncclCommInitRank: '), err\n"
+        "    print('rank', rank, 'refused')\n"
+        "    sys.exit(0)\n"
+        "assert rc == 0, lib.rr_last_error()\n"
         "whole = torch.arange(n, dtype=torch.float64, device='cuda') * 0.5\n"
         "mine = whole[a.value:b.value].clone()\n"
         "out = torch.zeros(n, dtype=torch.float64, device='cuda')\n"
@@ -501,9 +558,17 @@ def test_c_abi_allgather_over_rccl_two_ranks(tmp_path):
         "print('rank', rank, 'ok')\n" % REPO)
     idfile = str(tmp_path / "rccl.id")
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    procs = [subprocess.Popen([sys.executable, str(script), str(r), idfile],
+    procs = [subprocess.Popen([sys.executable, str(script), str(r), idfile,
+                               "1" if shared else "0"],
                               stdout=subprocess.PIPE, stderr=subprocess.STDOUT,
                               text=True, env=env) for r in range(2)]
-    outs = [p.communicate(timeout=300)[0] for p in procs]
+    try:
+        outs = [p.communicate(timeout=300)[0] for p in procs]
+    finally:
+        for p in procs:
+            if p.poll() is None:
+                p.kill()
+                p.wait()
     for r, (p, o) in enumerate(zip(procs, outs)):
-        assert p.returncode == 0 and "rank %d ok" % r in o, o[-2000:]
+        want = "rank %d %s" % (r, "refused" if shared else "ok")
+        assert p.returncode == 0 and want in o, o[-2000:]

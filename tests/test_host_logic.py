@@ -687,3 +687,44 @@ def test_monte_carlo_rejects_bad_exchange_before_touching_a_gpu():
     with pytest.raises(ValueError, match="qobs"):
         monte_carlo(ABCModel(), 5, sampler="device", return_qsim=False,
                     prec=prec)
+
+
+def test_bench_dump_outputs_is_bounded_and_fixed(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array the timed step handed its caller
+    as float64 .npy, within the byte limit (a sorted sample of the sets where
+    the whole does not fit, rows as well where one set's series does not),
+    the same sample on every run, and a manifest naming what was kept."""
+    import json
+    import types
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 200_000)
+    q = torch.arange(8000 * 1008, dtype=torch.float64).reshape(8000, 1008)
+    storages = (torch.rand(30, 5, 1000, dtype=torch.float64),
+                torch.rand(30, 1000, dtype=torch.float64))
+    r = {"sweep": types.SimpleNamespace(qsim=q[:, :1000], storages=storages),
+         "scores": torch.rand(1000, dtype=torch.float64), "steps": 4}
+    got = []
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), r)
+        names = sorted(os.listdir(tmp_path / str(k)))
+        assert names == ["manifest.json", "qsim.npy", "scores.npy",
+                         "storage0.npy", "storage1.npy"]
+        got.append({n: np.load(tmp_path / str(k) / n) for n in names
+                    if n.endswith(".npy")})
+        assert sum(a.nbytes for a in got[-1].values()) <= 200_000
+        assert all(a.dtype == np.float64 for a in got[-1].values())
+    assert all(np.array_equal(got[0][n], got[1][n]) for n in got[0])
+    with open(tmp_path / "0" / "manifest.json") as fh:
+        man = json.load(fh)
+    assert man["steps"] == 4
+    assert np.array_equal(got[0]["scores.npy"], r["scores"].numpy())
+    s1 = man["arrays"]["storage1"]
+    assert s1["shape"] == [30, 1000] and len(s1["sets"]) == s1[
+        "written_shape"][1] < 1000
+    assert np.array_equal(got[0]["storage1.npy"],
+                          storages[1][:, s1["sets"]].numpy())
+    qm = man["arrays"]["qsim"]            # one set's 8000 days exceed a share
+    flat = q[:, :1000][:, qm["sets"]].reshape(-1, len(qm["sets"]))
+    assert np.array_equal(got[0]["qsim.npy"],
+                          flat[qm["rows_of_flattened"]].numpy())
